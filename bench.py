@@ -610,7 +610,25 @@ def run_virtual_ranks(args, n_ranks, lits, shards, keep_rows=False):
     return out
 
 
-def run_workload(name, args, rank, world, dist, do_cpu):
+DUMP_MAX_RECORDS = 1 << 20  # --dump-outputs: records.npy (float64) + record_index.npy stay under 40 MiB
+
+
+def dump_outputs(ddir, recs):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in float64 (exact for the 32-bit fields).
+    records.npy: the match records, one row each (block, end, id, lit), in delivery order; above DUMP_MAX_RECORDS a fixed
+    seeded sample of them, and record_index.npy says which rows of the step's output they are.
+    matches_per_step.npy: the number of records the step produced."""
+    recs = np.asarray(recs).astype(np.uint32)
+    n = recs.shape[0]
+    idx = np.arange(n) if n <= DUMP_MAX_RECORDS else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_RECORDS, replace=False))
+    os.makedirs(ddir, exist_ok=True)
+    np.save(os.path.join(ddir, "records.npy"), recs[idx].astype(np.float64))
+    np.save(os.path.join(ddir, "record_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(ddir, "matches_per_step.npy"), np.array([n], dtype=np.float64))
+    log(f"outputs of the last timed step: {idx.size} of {n} records -> {ddir}")
+
+
+def run_workload(name, args, rank, world, dist, do_cpu, dump_dir=None):
     import torch
 
     total = int(args.gib * (1 << 30))
@@ -760,6 +778,10 @@ def run_workload(name, args, rank, world, dist, do_cpu):
         dist.barrier()
     dt = time.perf_counter() - t0
     assert all(jb.count() == n_matches for jb in jobs), "match count changed between repeats"  # hsbench main.cpp:778-787
+    last_out = None
+    if dump_dir and rank == 0:  # the last timed step's records (N > 1: as gathered), kept on the device until the end
+        last = (args.steps - 1) % depth
+        last_out = exch[last].compact()[0].clone() if exch is not None else jobs[last].d_out[: n_matches * 4].view(n_matches, 4).clone()
     dt_local, second_res = dt, None
     if second is not None:  # the other collective over the same K steps, same protocol (never `value`)
         ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -975,6 +997,9 @@ def run_workload(name, args, rank, world, dist, do_cpu):
         res["cpu_baseline"] = cpu
     if dist is None and depth == 1 and getattr(args, "sustain_seconds", 0) > 0:
         res["sustained"] = run_sustained(job, args.sustain_seconds, f"{name}, {job.total} bytes resident, serial steps")
+    if last_out is not None:
+        dump_outputs(dump_dir, last_out.cpu().numpy())
+        del last_out
     del job, jobs
     torch.cuda.empty_cache()
     return res
@@ -1710,7 +1735,12 @@ def main():
     ap.add_argument("--pipeline-depth", type=int, default=0, choices=[0, 1, 2],
                     help="scans in flight: 2 overlaps a step's record all-gather with the next step's scan; "
                          "0 = 1 at N = 1 (the per-kernel figures are then those of the kernels alone), 2 at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's last step's output (its match records) to DIR as .npy files "
+                         "(float64; at most 64 MB, a fixed seeded sample of a larger output): two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -1746,7 +1776,7 @@ def main():
     do_cpu = (rank == 0 and dist is None and not args.no_cpu)
     if args.scaling == "strong" and args.shards % world:
         raise SystemExit(f"bench.py: --shards {args.shards} is no multiple of {world} ranks")
-    main_res = run_workload(args.workload, args, rank, world, dist, do_cpu)
+    main_res = run_workload(args.workload, args, rank, world, dist, do_cpu, dump_dir=args.dump_outputs)
     also = {}
     if "sustained" in main_res:
         also["sustained"] = {"headline": main_res.pop("sustained")}

@@ -2,9 +2,10 @@
 (buildForwardAccel, src/rose/rose_build_lit_accel.cpp:372-465) and the shufti mask builder
 (shuftiBuildMasks, src/nfa/shufticompile.cpp:54-109) against the compiled reference."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
-import pytest
 
 import hyperscan_amd as H
 from hyperscan_amd import accel
@@ -109,17 +110,13 @@ def test_shufti_mask_builder_matches_reference():
     assert accel.CharClass(range(8)).to_shufti() is not None  # "always able to construct masks for 8 or fewer characters"
 
 
-def test_do_accel_block_model_is_the_reference_function():
-    """The expectation used for hsgpu_hwlm_forward_skip_dev on the GPU (tests/util.do_accel_block_model: the oracle's
-    accelerators inside a restatement of do_accel_block) against the reference's OWN static do_accel_block
-    (src/hwlm/hwlm.c:80-99, exported by oracle/ref_build/accel_block_shim.c which includes hwlm.c in place): every
-    scheme, buffers of 0 .. 400 bytes, every kind of `start` (0, inside, len - 16, len - 15, len)."""
-    from tests.util import do_accel_block_model
+DO_ACCEL_BLOCK_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "do_accel_block.json")
 
-    R = ob.href()
-    if not hasattr(R, "hsref_do_accel_block"):
-        pytest.skip("oracle/_ref predates the do_accel_block shim")
-    Lo = ob.hso()
+
+def do_accel_block_cases():
+    """The seeded inputs of test_do_accel_block_model_is_the_reference_function, in a fixed order: per literal set its
+    literals, its forward accelerator and the cases [(n, trial, block, starts)] -- also what
+    tools/make_do_accel_block_fixture.py runs the reference on for tests/golden/do_accel_block.json."""
     rng = np.random.default_rng(23)
     sets = [[L("needle", False, 0), L("xneed", False, 1)],                       # dverm
             [L("Hello", True, 0), L("shell", True, 1)],                          # dverm nocase
@@ -127,18 +124,10 @@ def test_do_accel_block_model_is_the_reference_function():
             [L("qa", False, 0), L("zq", False, 1)],                              # verm
             [L("Q", True, 0)],                                                   # verm nocase
             [L(bytes([0x80 + i, 0x41]), False, i) for i in range(12)]]           # high bytes: truffle or shufti
-    seen = set()
     for lits in sets:
         fa = accel.ForwardAccel.choose(lits)
-        assert fa.type != accel.ACCEL_NONE
-        seen.add(fa.type)
-        arr, _keep = pack_literals(list(lits))
-        out = (C.c_uint8 * 160)()
-        R.hsref_forward_accel(arr, len(arr), 0xFFFFFFFFFFFFFFFF, out)
-        img = (C.c_uint8 * 80).from_buffer_copy(bytes(out)[80:160])  # accel0: all groups
-        assert img[0] == fa.type and img[1] == fa.offset
-        kind, sc = fa.scanner()
         words = [l.s for l in lits] + [b"hello", b"SHELL", b"....", b"q", b"nee", b"\x80", b"A"]
+        cases = []
         for n in list(range(0, 40)) + [63, 64, 65, 100, 257, 400]:
             for trial in range(6):
                 text = b"".join(words[int(i)] + b"." * int(rng.integers(0, 12)) for i in rng.integers(0, len(words), n // 3 + 1))
@@ -147,8 +136,49 @@ def test_do_accel_block_model_is_the_reference_function():
                     blk[:] = ord("~")            # nothing to find
                 if trial == 1 and n:
                     blk[-1] = lits[0].s[0]       # the last byte alone: double vermicelli's partial match
-                for start in sorted(x for x in {0, 1, n // 2, max(0, n - 17), max(0, n - 16), max(0, n - 15), n} if x <= n):  # (hwlmExec: start <= len)
-                    want = R.hsref_do_accel_block(img, blk.ctypes.data, n, start)
-                    got = do_accel_block_model(Lo, kind, sc, fa.offset, blk, start)
-                    assert got == want, (fa.type, n, start, trial, got, want)
+                starts = sorted(x for x in {0, 1, n // 2, max(0, n - 17), max(0, n - 16), max(0, n - 15), n} if x <= n)  # (hwlmExec: start <= len)
+                cases.append((n, trial, blk, starts))
+        yield lits, fa, cases
+
+
+def reference_accel_image(R, lits):
+    """the reference's decoded AccelAux for all groups (accel0 of hsref_forward_accel), 80 bytes"""
+    arr, _keep = pack_literals(list(lits))
+    out = (C.c_uint8 * 160)()
+    R.hsref_forward_accel(arr, len(arr), 0xFFFFFFFFFFFFFFFF, out)
+    return bytes(out)[80:160]
+
+
+def test_do_accel_block_model_is_the_reference_function():
+    """The expectation used for hsgpu_hwlm_forward_skip_dev on the GPU (tests/util.do_accel_block_model: the oracle's
+    accelerators inside a restatement of do_accel_block) against the reference's OWN static do_accel_block
+    (src/hwlm/hwlm.c:80-99, exported by oracle/ref_build/accel_block_shim.c which includes hwlm.c in place): every
+    scheme, buffers of 0 .. 400 bytes, every kind of `start` (0, inside, len - 16, len - 15, len). The reference's answers
+    are stored in tests/golden/do_accel_block.json; where oracle/_ref is built, the reference itself is asked as well and
+    must give the stored answers."""
+    from tests.util import do_accel_block_model
+
+    golden = json.load(open(DO_ACCEL_BLOCK_GOLDEN))["sets"]
+    R = ob.href() if ob.ref_available() else None
+    live = R is not None and hasattr(R, "hsref_do_accel_block")
+    Lo = ob.hso()
+    seen = set()
+    for (lits, fa, cases), g in zip(do_accel_block_cases(), golden, strict=True):
+        assert fa.type != accel.ACCEL_NONE
+        seen.add(fa.type)
+        raw = bytes.fromhex(g["image_hex"])
+        if live:
+            assert reference_accel_image(R, lits) == raw
+        img = (C.c_uint8 * 80).from_buffer_copy(raw)
+        assert img[0] == fa.type and img[1] == fa.offset
+        kind, sc = fa.scanner()
+        want_all = iter(g["want"])
+        for n, trial, blk, starts in cases:
+            for start in starts:
+                want = next(want_all)
+                if live:
+                    assert R.hsref_do_accel_block(img, blk.ctypes.data, n, start) == want, (fa.type, n, start, trial)
+                got = do_accel_block_model(Lo, kind, sc, fa.offset, blk, start)
+                assert got == want, (fa.type, n, start, trial, got, want)
+        assert next(want_all, None) is None, "tests/golden/do_accel_block.json holds more cases than the test makes"
     assert {accel.ACCEL_DVERM, accel.ACCEL_DVERM_NOCASE, accel.ACCEL_SHUFTI, accel.ACCEL_VERM, accel.ACCEL_VERM_NOCASE} <= seen

@@ -260,14 +260,18 @@ def test_hs_scan_per_packet_through_the_small_batch_server(mailbox):
             at = int(rng.integers(0, n - len(w)))
             p[at:at + len(w)] = w
         packets.append(bytes(p))
-    total_events = 0
-    for k, p in enumerate(packets):
-        a, b = collect(db, p, plain), collect(db, p, served)
-        assert a == b, (k, len(p))
-        total_events += len(a)
-    assert total_events > 100
+    # the served calls as one burst, then the same packets on the scratch without a server: a kernel on another stream can wait
+    # behind the resident workgroup until that goes idle (where the two streams share a hardware queue), which ends the server
+    # between two calls of the burst
+    served_events = [collect(db, p, served) for p in packets]
     calls, launches = served.server_stats()
     assert calls >= 150 and launches <= 6, (calls, launches)
+    total_events = 0
+    for k, p in enumerate(packets):
+        a = collect(db, p, plain)
+        assert a == served_events[k], (k, len(p))
+        total_events += len(a)
+    assert total_events > 100
     # ... and as one batch
     off = np.concatenate([[0], np.cumsum([len(p) for p in packets])]).astype(np.uint64)
     got = []
